@@ -21,6 +21,12 @@ no collective in the data path).  Every rank keeps the raw fp64 NMSE_Split sums 
 step; after the timed loop one all_reduce gives each step's ratio over the whole global batch, and
 one all_gather collates the last step's predictions on rank 0, which reduces NMSE_Split over them
 itself and checks it against the all-reduced sums.  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline needs: set-up, warm-up, the ``--steps`` timed steps, the all-reduced NMSE and
+the result line.  ``--full`` adds the kernel-alone timing with the roofline block, the parity spot check against
+the CPU oracle, the gathered-prediction NMSE check and the CPU baseline.  The sampler chains are reseeded at the
+end of the warm-up, so with the same arguments every run feeds the timed steps the same inputs and draws;
+``--dump-outputs DIR`` writes what the last timed step computed (``out.npy``, ``nmse_sums.npy``).
 """
 from __future__ import annotations
 
@@ -153,7 +159,31 @@ def parse_args(argv=None):
                     help="NMSE_Split in the forward's epilogue (cet_forward_nmse) or as its own launch")
     ap.add_argument("--collation-selftest", action="store_true",
                     help="CPU/gloo rehearsal of the multi-rank spawn and NMSE collation (no GPU, no engine)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the kernel-alone "
+                         "timing and roofline block, the parity spot check against the CPU oracle, the NMSE check "
+                         "over the gathered predictions and the CPU baseline (see --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR: out.npy (float32 predictions of the "
+                         "global batch, rank order) and nmse_sums.npy (float64 [2, pred_len] raw NMSE_Split sums)")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET = 64 << 20        # bytes --dump-outputs may write in all
+
+
+def dump_outputs(path, arrays):
+    """Write each array as ``path/<name>.npy`` (float32 stays float32, anything else goes to float64).  Past the
+    budget an array is cut to a fixed, seeded sample of its rows, the same rows in every run."""
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET
+    for name, a in sorted(arrays.items(), key=lambda kv: kv[1].nbytes):
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > left:
+            keep = max(1, left // max(a.nbytes // a.shape[0], 1))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        left -= a.nbytes
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def collate_and_report(sums, out_last, lab, world, rank, nmse_fn):
@@ -274,6 +304,14 @@ def main(argv=None):
             n_warm += 1
         if n_warm >= args.warmup:
             torch.cuda.synchronize(dev)
+    # the settle loop runs by the clock, so the sampler chains are reseeded here: the timed steps consume the same
+    # draws in every run.  One more untimed step per lane takes the reseed's state upload and first table launch
+    torch.cuda.synchronize(dev)
+    for i, ln in enumerate(lanes):
+        ln["eng"].seed(1 + i)
+    for i in range(NL):
+        step(-1, i)
+        n_warm += 1
     torch.cuda.synchronize(dev)
     if dist:
         dist.barrier()
@@ -292,30 +330,31 @@ def main(argv=None):
     if path != "v4":
         raise SystemExit(f"the timed steps ran the {path} path, not the fused v4 kernel")
     kernel_name = eng.last_kernel()       # its instance (the C2 one when the plan is C2's: plan_is_c2)
-    # the kernel alone, after the timed loop (roofline.kernel_ms): lane 0's forward launches back to back on
-    # its stream with nothing else in flight, one event pair around KALONE launches (the forward only: with
-    # --nmse separate the reduction's launch is left out)
-    ln0 = lanes[0]
-    st0 = ln0["stream"]
+    if args.full:
+        # the kernel alone, after the timed loop (roofline.kernel_ms): lane 0's forward launches back to back on
+        # its stream with nothing else in flight, one event pair around KALONE launches (the forward only: with
+        # --nmse separate the reduction's launch is left out)
+        ln0 = lanes[0]
+        st0 = ln0["stream"]
 
-    def forward_only():
-        if args.nmse == "fused":
-            ln0["fused"](args.steps)
-        else:
-            with torch.cuda.stream(st0):
-                ln0["eng"].forward(ln0["xe"], ln0["xd"], ln0["out"], None, st0.cuda_stream)
-    for _ in range(16):   # the clock is still at its loaded level: the timed loop just ended
-        forward_only()
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize(dev)
-    ev0.record(st0)
-    for _ in range(KALONE):
-        forward_only()
-    ev1.record(st0)
-    torch.cuda.synchronize(dev)
-    kern_ms, launches = ev0.elapsed_time(ev1), KALONE
-    if eng.last_kernel() != kernel_name:
-        raise SystemExit(f"the kernel-alone loop ran {eng.last_kernel()}, the timed steps {kernel_name}")
+        def forward_only():
+            if args.nmse == "fused":
+                ln0["fused"](args.steps)
+            else:
+                with torch.cuda.stream(st0):
+                    ln0["eng"].forward(ln0["xe"], ln0["xd"], ln0["out"], None, st0.cuda_stream)
+        for _ in range(16):   # the clock is still at its loaded level: the timed loop just ended
+            forward_only()
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(dev)
+        ev0.record(st0)
+        for _ in range(KALONE):
+            forward_only()
+        ev1.record(st0)
+        torch.cuda.synchronize(dev)
+        kern_ms, launches = ev0.elapsed_time(ev1), KALONE
+        if eng.last_kernel() != kernel_name:
+            raise SystemExit(f"the kernel-alone loop ran {eng.last_kernel()}, the timed steps {kernel_name}")
 
     per_rank = [dt_rank]
     if dist:
@@ -323,11 +362,46 @@ def main(argv=None):
         dist.all_gather(allt, torch.tensor([dt_rank], dtype=torch.float64, device=dev))
         per_rank = [float(t.item()) for t in allt]
     dt = max(per_rank)
-    nmse, check = collate_and_report(sums, out_last, last["lab"], world, rank, lambda p, y: nmse_split(p, y))
+    from channelestimationtransformer_amd.sharding import collate_step_sums, gather_predictions
+
+    if args.full:
+        nmse, check = collate_and_report(sums, out_last, last["lab"], world, rank, lambda p, y: nmse_split(p, y))
+    else:   # the headline's NMSE needs the all-reduced sums only
+        nmse = collate_step_sums(sums, world)[1].cpu().numpy()
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step: the predictions (all ranks', rank order)
+        # and the raw NMSE_Split sums of that step over the global batch
+        preds = gather_predictions(out_last, world)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"out": torch.cat(preds).cpu().numpy(),
+                                             "nmse_sums": sums[args.steps - 1].cpu().numpy()})
 
     if rank == 0:
-        flops = informer_flops()
         seqs = B * world * args.steps
+        res = {
+            "metric": METRIC,
+            "value": round(seqs / dt, 1),
+            "unit": "seq/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "bf16",
+            "data": "synthetic (seeded Jakes channels, SNR %g dB; seeded synthetic weights)" % args.snr,
+            "config": {"workload": WORKLOAD, "batch_per_gpu": B, "global_batch": B * world,
+                       "parallelism": f"dp{world}", "nmse": args.nmse,
+                       "inflight_batches_per_gpu": NL},
+            "world": world,
+            "backend": "nccl" if world > 1 else None,
+            "per_rank_ms_per_step": [round(t / args.steps * 1e3, 4) for t in per_rank],
+            "warmup_steps_run": n_warm,
+            "nmse_db": [round(float(10 * np.log10(v)), 3) for v in nmse],
+        }
+    if rank == 0 and args.full:
+        flops = informer_flops()
         avg_kernel_s = kern_ms / 1e3 / max(launches, 1)
         achieved = flops * B / avg_kernel_s / 1e12
         # parity spot check of this very engine against the CPU oracle (8 sequences, fixed draws)
@@ -352,27 +426,7 @@ def main(argv=None):
         except Exception as exc:  # pragma: no cover - reported, not fatal
             parity = f"error: {exc}"
         traffic, traffic_src = load_traffic(os.path.join(ROOT, "profiles"), kernel_name)
-        res = {
-            "metric": METRIC,
-            "value": round(seqs / dt, 1),
-            "unit": "seq/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "bf16",
-            "data": "synthetic (seeded Jakes channels, SNR %g dB; seeded synthetic weights)" % args.snr,
-            "config": {"workload": WORKLOAD, "batch_per_gpu": B, "global_batch": B * world,
-                       "parallelism": f"dp{world}", "nmse": args.nmse,
-                       "inflight_batches_per_gpu": NL},
-            "world": world,
-            "backend": "nccl" if world > 1 else None,
-            "per_rank_ms_per_step": [round(t / args.steps * 1e3, 4) for t in per_rank],
-            "warmup_steps_run": n_warm,
-            "nmse_db": [round(float(10 * np.log10(v)), 3) for v in nmse],
+        res.update({
             "nmse_gathered_vs_allreduced_rel": check,
             "parity_rel_nmse_vs_oracle": parity,
             "roofline": {"bound": "mfma", "achieved": round(achieved, 3), "peak": PEAK_BF16_TFLOPS,
@@ -387,9 +441,10 @@ def main(argv=None):
                          "frac_effective": round(flops * seqs / dt / 1e12 / PEAK_BF16_TFLOPS, 5),
                          "flops_per_seq": flops, "io_bytes_per_seq": io_bytes(),
                          "hbm_achieved_gbps": round(io_bytes() * B / avg_kernel_s / 1e9, 2)},
-        }
+        })
         if not args.no_cpu_baseline and world == 1:   # the CPU leg: rank 0 at N=1 only
             res["cpu_baseline"] = cpu_baseline(B)
+    if rank == 0:
         print(json.dumps(res), flush=True)
     if dist:
         dist.barrier()

@@ -54,6 +54,23 @@ def load_case(name: str) -> Case:
     return Case(name, meta, z, state, idx)
 
 
+def load_mimo_checkpoint():
+    """The reference's trained MimoSimulation checkpoint (models/checkpoint/checkpoint.pth) from its fixture
+    parts (tests/golden/make_checkpoint_golden.py): every part is a ``{"state_dict": ...}`` file read as the
+    callers read the original; a key met again continues that tensor along dim 1."""
+    import torch
+
+    sd, n = {}, 0
+    while os.path.exists(os.path.join(GOLDEN, f"mimo_checkpoint.part{n}.pth")):
+        part = torch.load(os.path.join(GOLDEN, f"mimo_checkpoint.part{n}.pth"), weights_only=True,
+                          map_location="cpu")["state_dict"]
+        for k, v in part.items():
+            sd[k] = torch.cat([sd[k], v], 1) if k in sd else v
+        n += 1
+    assert n, "tests/golden/mimo_checkpoint.part*.pth missing"
+    return sd
+
+
 def informer_oracle_config(cfg: dict, lsq_bits=None, stack=True):
     """Effective oracle flags for the callers' 19/20-positional-argument construction."""
     from oracle.informer_np import InformerConfig

@@ -50,17 +50,13 @@ def test_trained_mimo_checkpoint_drops_into_the_engine():
     loaded by MimoSimulation/Predict.py:91-93 for InformerStack(16,16,16, 25,10,5, 5, d_model 64, 8,
     e_layers [4,3], 3, 64, attn "full")): read with torch.load(weights_only=True), loaded with the
     callers' strict=False, and planned by the layer-wise engine (d_model 64 is outside the fused
-    kernels).  Host only; skipped where the reference tree is absent (it never travels)."""
-    import os
-
-    import pytest
-
-    path = "/root/reference/MimoSimulation/models/checkpoint/checkpoint.pth"
-    if not os.path.exists(path):
-        pytest.skip("reference tree absent")
+    kernels).  Host only.  The 4.1 MB file is committed as fixture parts of the same format
+    (tests/golden/mimo_checkpoint.part*.pth, golden_util.load_mimo_checkpoint)."""
     from channelestimationtransformer_amd.engine import Engine
+    from golden_util import load_mimo_checkpoint
 
-    sd = torch.load(path, weights_only=True, map_location="cpu")["state_dict"]
+    sd = load_mimo_checkpoint()
+    assert len(sd) == 239 and sum(v.numel() * v.element_size() for v in sd.values()) == 4052840
     m = InformerStack(16, 16, 16, 25, 10, 5, 5, 64, 8, [4, 3], 3, 64, 0.05, "full", "fixed", "gelu", True, True,
                       torch.device("cpu"))
     res = m.load_state_dict(sd, strict=False)

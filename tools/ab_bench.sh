@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT"
 for i in $(seq 1 ${AB_ROUNDS:-2}); do
   for lib in "$@"; do
-    r=$(CET_LIB=$(pwd)/$lib timeout -k 10 120 python bench.py --steps 300 --warmup 100 --no-cpu-baseline $BENCH_ARGS 2>/dev/null | tail -1) || exit 1
+    r=$(CET_LIB=$(pwd)/$lib timeout -k 10 120 python bench.py --full --steps 300 --warmup 100 --no-cpu-baseline $BENCH_ARGS 2>/dev/null | tail -1) || exit 1
     echo "$lib: $(echo "$r" | python -c "import json,sys;d=json.loads(sys.stdin.read());print(d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])")"
   done
 done

@@ -33,11 +33,11 @@ for s in "$@"; do
       $T 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.txt" 2>&1 || { cat "$O/smoke.txt"; exit 1; }
       cat "$O/smoke.txt" ;;
     bench1)
-      $T 300 python bench.py --inflight 1 --no-cpu-baseline > "$O/bench_inflight1.json" 2> "$O/bench1.err" \
+      $T 300 python bench.py --full --inflight 1 --no-cpu-baseline > "$O/bench_inflight1.json" 2> "$O/bench1.err" \
         || { tail -20 "$O/bench1.err"; exit 1; }
       cut -c1-400 "$O/bench_inflight1.json" ;;
     bench2)
-      $T 300 python bench.py > "$O/bench.json" 2> "$O/bench2.err" || { tail -20 "$O/bench2.err"; exit 1; }
+      $T 300 python bench.py --full > "$O/bench.json" 2> "$O/bench2.err" || { tail -20 "$O/bench2.err"; exit 1; }
       cut -c1-400 "$O/bench.json" ;;
     prof)
       (cd /tmp && $T 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof_if1" -o trace -- \
